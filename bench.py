@@ -4,6 +4,10 @@ Msamples/sec (+ Mrays/sec), San Miguel 1080p; the scene itself is not available 
 workload is the San-Miguel-class synthetic stand-in of SURVEY.md s.8(d), generated deterministically).
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched under torch.distributed.run)
+  python bench.py ... --full                           (+ roofline, CPU baselines, parity crop, secondary workload)
+  python bench.py ... --dump-outputs DIR               (+ the last timed step's film as DIR/film.npy)
+
+A plain run sets up, warms up (W plain steps), times the K steps and prints the line; everything else it can measure is behind --full.
 
 A "step" = one full pass of the hot path (SamplerIntegrator::Render: 1920x1080 x 64 spp, path maxdepth 5)
 over the frame with the scene already resident in HBM.  With N>1 the 16x16 image tiles are sharded over the
@@ -31,10 +35,26 @@ NODE_BYTES, TRI_BYTES, RAY_BYTES = 128, 48, 48   # algorithmic bytes (DESIGN.md 
 # tools/valu_probe/valu_probe2 on the MI355X (profiles/r04_a_valu_probe2_issue_rate_and_clock.txt), 8 waves per SIMD, host-event time x measured clock:
 PROBE_MIX_CYCLES = 3.39   # cycles per wave instruction per SIMD of the box test's instruction mix (kind 3: 1.430 ns at 2.372 GHz)
 PROBE_FMA_CYCLES = 2.22   # ... of independent v_fma_f32 (kind 0: 1.049 ns at 2.114 GHz)
+DUMP_BYTES = 64 * 10**6   # --dump-outputs: at most this many bytes of arrays in all
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(d, film):
+    """--dump-outputs: the film of the last timed step (H, W, 4 float32) as d/film.npy; a film over DUMP_BYTES as a fixed sample of its pixels
+    (seed 0, the same pixels for the same --res): d/film_sample.npy (n, 4 float32) and their flat pixel indices d/film_pixels.npy (float64)"""
+    os.makedirs(d, exist_ok=True)
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.nbytes + 4096 <= DUMP_BYTES:
+        np.save(os.path.join(d, "film.npy"), film)
+        return
+    px = film.reshape(-1, 4)
+    n = (DUMP_BYTES - 4096) // (px.itemsize * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(d, "film_sample.npy"), px[idx])
+    np.save(os.path.join(d, "film_pixels.npy"), idx.astype(np.float64))
 
 
 _T0 = time.time()
@@ -221,7 +241,7 @@ def valu_live(wl_args, pmc_steps=1):
 
 def secondary_line(extra):
     """bench.py itself on a variant workload, 3 steps after 1 warm-up, with a short pbrt_ref crop at full spp; returns the fields of its JSON line worth keeping"""
-    cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--steps", "3", "--warmup", "1", "--traffic", "none", "--cpu-seconds", "8", "--cpu-port-seconds", "0", "--secondary", "off"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--steps", "3", "--warmup", "1", "--traffic", "none", "--cpu-seconds", "8", "--cpu-port-seconds", "0", "--secondary", "off"]
     t0 = time.time()
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
@@ -372,6 +392,13 @@ def main():
     ap.add_argument("--leafmask", action="store_true", help="c3 only: the stand-in's leaf quads as alpha-masked meshes (a disc cut out of each by a float texture; SURVEY.md s.8 row f2 alpha masks), combinable with --volpath / --fogbox")
     ap.add_argument("--fogbox", action="store_true", help="c3 only: a bank of fog behind a BSDF-less box in the far half of the stand-in, Integrator \"volpath\" (medium interfaces: k_vol_tr)")
     ap.add_argument("--volpath", action="store_true", help="c3 only: the stand-in inside a homogeneous medium, Integrator \"volpath\" (SURVEY.md s.8 row f4; k_shade_vol)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: a counting pass (as the first warm-up step) feeding the roofline, the rocprofv3 --pmc passes, "
+                         "the stream-read / gather ceilings, the CPU baselines with the parity crop against pbrt_ref and the secondary workload. Without it a run "
+                         "sets up, warms up, times --steps, dumps and prints the line; --cpu-seconds, --cpu-port-seconds, --traffic, --save-traffic and --secondary apply with --full only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path computed in its last step as DIR/film.npy (H, W, 4 float32: contribSum rgb, filterWeightSum); a film over "
+                         "%d MB as a fixed sample of its pixels (film_sample.npy + their flat indices film_pixels.npy)" % (DUMP_BYTES // 10**6))
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target length of the CPU baseline sample: the reference binary oracle/_ref/pbrt_ref on a centre crop of the same frame (0 = skip)")
     ap.add_argument("--cpu-port-seconds", type=float, default=6.0, help="length of the second CPU sample, the oracle port (0 = skip)")
     ap.add_argument("--traffic", default="live", choices=["live", "file", "none"],
@@ -387,6 +414,8 @@ def main():
     ap.add_argument("--one-device", action="store_true", help="testing aid: every rank uses GPU 0 (device ordinal only: local rank 0 still builds the scene alone, the others map it)")
     ap.add_argument("--dump-film", default=None, help="rank 0 saves the combined FilmTilePixel array (H, W, 4 float32: contribSum rgb, filterWeightSum) of the last timed step as .npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU under torch.distributed.run, the
@@ -520,18 +549,22 @@ def main():
         ctx.close()
         return
 
-    # ---- one counting pass (deterministic work: node / triangle fetch counts feed the roofline), then warm-up
-    ctx.counters_reset()
-    step(count=True)
-    sync_all()
-    work = ctx.counters()
-    phase("counting pass done")
-    try:
-        trace_clk = ctx.trace_clock()   # shader clock inside the traversal launches of the counting pass (s_memtime / s_memrealtime per wave)
-    except Exception:
-        trace_clk = None
-    for _ in range(max(0, args.warmup - 1)):
-        step()
+    if args.full:
+        # ---- one counting pass (deterministic work: node / triangle fetch counts feed the roofline), then warm-up
+        ctx.counters_reset()
+        step(count=True)
+        sync_all()
+        work = ctx.counters()
+        phase("counting pass done")
+        try:
+            trace_clk = ctx.trace_clock()   # shader clock inside the traversal launches of the counting pass (s_memtime / s_memrealtime per wave)
+        except Exception:
+            trace_clk = None
+        for _ in range(max(0, args.warmup - 1)):
+            step()
+    else:
+        for _ in range(args.warmup):
+            step()
     sync_all()
 
     # ---- timed region: exactly K steps
@@ -544,8 +577,13 @@ def main():
     sync_all()
     elapsed = frame.max_over_ranks(time.perf_counter() - t0)
     phase("%d timed step(s) done: %.1f ms per step" % (args.steps, elapsed / max(1, args.steps) * 1e3))
-    if args.dump_film and rank == 0:
-        np.save(args.dump_film, frame.root_film())
+    if (args.dump_film or args.dump_outputs) and rank == 0:
+        film = frame.root_film()
+        if args.dump_film:
+            np.save(args.dump_film, film)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, film)
+        del film
     timing = ctx.timing()
     cnt = ctx.counters()
     if cnt.get("trace_guard_trips", 0):
@@ -558,138 +596,140 @@ def main():
     if rank == 0:
         msamples = samples[0] / elapsed * 1e-6
         mrays = samples[1] / elapsed * 1e-6
-        # ---- roofline of the dominant kernel (closest-hit traversal of path-extension rays), this rank.
-        # `achieved` = HBM-side bytes per launch (rocprofv3 --pmc: the L2's memory-side read requests by size, traffic_live -- what the guide's
-        # "FETCH_SIZE x 2" amounts to on gfx950, calibrated in round 5) / the live average launch time (HIP events on the ctx stream): a true fraction of the
-        # 8 TB/s peak.  The ALGORITHMIC byte rate of SURVEY.md s.8(d) (every node / triangle fetch counted, most of them
-        # served by the XCD L2s) is reported beside it as l2_served_GBps -- it exceeds the HBM peak and bounds nothing.
-        n_launch = max(1, timing["closest"][1])
-        ext_rays = work["closest_rays"] - work["mis_rays"]
-        tinfo = ctx.trace_info()
-        alg_bytes = ext_rays * RAY_BYTES + work["nodes_closest"] * tinfo["node_bytes"] + work["tris_closest"] * TRI_BYTES   # per step
-        t_closest_ms = timing["closest"][0] / args.steps                                                           # per step
-        launches_per_step = n_launch / args.steps
-        avg_launch_ms = t_closest_ms / max(1.0, launches_per_step)
-        alg_rate = alg_bytes / (t_closest_ms * 1e-3) * 1e-9 if t_closest_ms > 0 else 0.0
-        wl_args = ["--config", args.config, "--tris", str(args.tris), "--res", str(args.res[0]), str(args.res[1]), "--spp", str(args.spp)]
-        if args.scene:
-            wl_args += ["--scene", args.scene]
-        if args.textured:
-            wl_args += ["--textured"]
-        if args.volpath:
-            wl_args += ["--volpath"]
-        if args.fogbox:
-            wl_args += ["--fogbox"]
-        if args.leafmask:
-            wl_args += ["--leafmask"]
-        if args.subsurface:
-            wl_args += ["--subsurface"]
-        if args.smokebox:
-            wl_args += ["--smokebox"]
-        if args.max_paths:
-            wl_args += ["--max-paths", str(args.max_paths)]
-        traffic = None
-        roofline_shade = None
-        if world == 1 and args.traffic == "live":
-            traffic = traffic_live(wl_args, workload, 1 if args.config == "c5" else 2)
-        if world == 1 and traffic is None and args.traffic in ("live", "file"):
-            traffic = traffic_from_file(workload)
-        if traffic and args.save_traffic and traffic.get("source", "").startswith("live"):
-            traffic_save(workload, traffic)
-        roofline = {"kernel": (traffic or {}).get("kernel", "k_trace<0, ...> (BVH4 closest hit, path-extension rays)"), "bound": "hbm",
-                    "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
-                    "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_source": traffic["source"] if traffic else None,
-                    "avg_launch_ms": avg_launch_ms, "launches_per_step": launches_per_step,
-                    "alg_bytes_per_launch": alg_bytes / max(1.0, launches_per_step), "l2_served_GBps": round(alg_rate, 1),
-                    "nodes_per_ray": work["nodes_closest"] / max(1, ext_rays), "tris_per_ray": work["tris_closest"] / max(1, ext_rays),
-                    "layout": "%s: %d nodes x %d B" % (tinfo["name"], tinfo["nodes"], tinfo["node_bytes"]),
-                    # interior steps served from the traversal blocks' LDS copy of the scene's most visited nodes (hot-node probe at upload)
-                    "hot_nodes_in_lds": tinfo.get("hot_nodes", 0), "hot_share_of_node_visits": round(work.get("nodes_hot_closest", 0) / max(1, work["nodes_closest"]), 4),
-                    "launch_shape": "%d threads x %d block(s) per CU" % (tinfo.get("block_threads", 256), tinfo.get("blocks_per_cu", 6))}
-        if traffic:
-            roofline["achieved"] = round(traffic["bytes_per_launch"] / (avg_launch_ms * 1e-3) * 1e-9, 1)
-            roofline["frac"] = round(roofline["achieved"] / HBM_PEAK_GBS, 4)
-            roofline["alg_over_hbm_bytes"] = round(roofline["alg_bytes_per_launch"] / traffic["bytes_per_launch"], 2)
-        try:
-            roofline["hbm_stream_read_GBps"] = round(ctx.stream_read_gbps(4 << 30), 1)   # achievable ceiling, beside the spec peak
-            if roofline["achieved"]:
-                roofline["frac_of_stream_ceiling"] = round(roofline["achieved"] / roofline["hbm_stream_read_GBps"], 4)
-        except Exception as e:   # measurement aid only
-            log("[bench] stream-read ceiling not measured: %s" % e)
-        # What the traversal IS bound by: the rate at which a CU serves incoherent 16-byte loads.  achieved = the kernel's own
-        # lane requests (node words + triangle vertices + the ray record, from the counting pass) / its launch time; ceiling = mi_gather_rate:
-        # chains of dependent random fetches of records of the node size from a buffer of the node array's size, same launch shape, no arithmetic.
-        try:
-            loads = max(1, min(4, tinfo["node_bytes"] // 16))
-            # vector-memory lane requests: the node steps NOT served from LDS, the triangle vertices, the ray record
-            req_per_step = (work["nodes_closest"] - work.get("nodes_hot_closest", 0)) * (tinfo["node_bytes"] // 16) + work["tris_closest"] * 3 + ext_rays * 3
-            ach = req_per_step / (t_closest_ms * 1e-3) * 1e-9 if t_closest_ms > 0 else 0.0
-            node_mb = max(1, (tinfo["nodes"] * tinfo["node_bytes"]) >> 20)
-            ladder = {}   # the same chain of dependent record fetches over working sets that sit in the L1s, the L2s, the Infinity Cache, HBM
-            for name, nbytes in (("L1_32KB", 32 << 10), ("L2_2MB", 2 << 20), ("MALL_64MB", 64 << 20), ("HBM_%dMB_node_array" % node_mb, node_mb << 20)):
-                ladder[name] = round(ctx.gather_rate(nbytes, loads), 1)
-            roofline["request_rate"] = {"achieved_Greq_per_s": round(ach, 1), "requests_per_ray": round(req_per_step / max(1, ext_rays), 1),
-                                        "ceilings_Greq_per_s": ladder, "frac_of_L2_resident_ceiling": round(ach / ladder["L2_2MB"], 4) if ladder["L2_2MB"] > 0 else None,
-                                        "ceilings_are": "mi_gather_rate: chains of dependent random %d x 16 B record fetches per lane over a buffer of the stated size, "
-                                                        "traversal launch shape, no arithmetic; the traversal's own fetches are a MIX of these levels (upper tree levels are shared)" % loads}
-        except Exception as e:   # measurement aid only
-            log("[bench] request-rate ceiling not measured: %s" % e)
-        # ... and what does bound it: VALU issue.  Everything here is measured: the launch's SIMD cycles = live launch time x the shader
-        # clock the kernel itself reports (s_memtime / s_memrealtime per wave, mi_trace_clock); its VALU instructions per SIMD from a separate rocprofv3 --pmc
-        # pass; the ceiling from tools/valu_probe (profiles/r04_a_valu_probe2_issue_rate_and_clock.txt: a SIMD issues the box test's instruction mix at
-        # 3.39 cycles per wave instruction with 8 waves resident, plain v_fma_f32 at 2.2; profiles/r04_c_issue_probe_instruction_costs.txt per instruction).
-        clk_ghz = (trace_clk or {}).get("closest_GHz") or 0.0
-        if clk_ghz:
-            roofline["shader_clock_GHz"] = {"closest": round(trace_clk["closest_GHz"], 3), "anyhit": round(trace_clk["anyhit_GHz"], 3),
-                                            "source": "s_memtime / s_memrealtime ticks per wave inside the launches of the counting pass (mi_trace_clock)"}
-        if world == 1 and args.traffic == "live":
+        roofline = roofline_shade = None
+        if args.full:
+            # ---- roofline of the dominant kernel (closest-hit traversal of path-extension rays), this rank.
+            # `achieved` = HBM-side bytes per launch (rocprofv3 --pmc: the L2's memory-side read requests by size, traffic_live -- what the guide's
+            # "FETCH_SIZE x 2" amounts to on gfx950, calibrated in round 5) / the live average launch time (HIP events on the ctx stream): a true fraction of the
+            # 8 TB/s peak.  The ALGORITHMIC byte rate of SURVEY.md s.8(d) (every node / triangle fetch counted, most of them
+            # served by the XCD L2s) is reported beside it as l2_served_GBps -- it exceeds the HBM peak and bounds nothing.
+            n_launch = max(1, timing["closest"][1])
+            ext_rays = work["closest_rays"] - work["mis_rays"]
+            tinfo = ctx.trace_info()
+            alg_bytes = ext_rays * RAY_BYTES + work["nodes_closest"] * tinfo["node_bytes"] + work["tris_closest"] * TRI_BYTES   # per step
+            t_closest_ms = timing["closest"][0] / args.steps                                                           # per step
+            launches_per_step = n_launch / args.steps
+            avg_launch_ms = t_closest_ms / max(1.0, launches_per_step)
+            alg_rate = alg_bytes / (t_closest_ms * 1e-3) * 1e-9 if t_closest_ms > 0 else 0.0
+            wl_args = ["--config", args.config, "--tris", str(args.tris), "--res", str(args.res[0]), str(args.res[1]), "--spp", str(args.spp)]
+            if args.scene:
+                wl_args += ["--scene", args.scene]
+            if args.textured:
+                wl_args += ["--textured"]
+            if args.volpath:
+                wl_args += ["--volpath"]
+            if args.fogbox:
+                wl_args += ["--fogbox"]
+            if args.leafmask:
+                wl_args += ["--leafmask"]
+            if args.subsurface:
+                wl_args += ["--subsurface"]
+            if args.smokebox:
+                wl_args += ["--smokebox"]
+            if args.max_paths:
+                wl_args += ["--max-paths", str(args.max_paths)]
+            traffic = None
+            roofline_shade = None
+            if world == 1 and args.traffic == "live":
+                traffic = traffic_live(wl_args, workload, 1 if args.config == "c5" else 2)
+            if world == 1 and traffic is None and args.traffic in ("live", "file"):
+                traffic = traffic_from_file(workload)
+            if traffic and args.save_traffic and traffic.get("source", "").startswith("live"):
+                traffic_save(workload, traffic)
+            roofline = {"kernel": (traffic or {}).get("kernel", "k_trace<0, ...> (BVH4 closest hit, path-extension rays)"), "bound": "hbm",
+                        "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                        "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_source": traffic["source"] if traffic else None,
+                        "avg_launch_ms": avg_launch_ms, "launches_per_step": launches_per_step,
+                        "alg_bytes_per_launch": alg_bytes / max(1.0, launches_per_step), "l2_served_GBps": round(alg_rate, 1),
+                        "nodes_per_ray": work["nodes_closest"] / max(1, ext_rays), "tris_per_ray": work["tris_closest"] / max(1, ext_rays),
+                        "layout": "%s: %d nodes x %d B" % (tinfo["name"], tinfo["nodes"], tinfo["node_bytes"]),
+                        # interior steps served from the traversal blocks' LDS copy of the scene's most visited nodes (hot-node probe at upload)
+                        "hot_nodes_in_lds": tinfo.get("hot_nodes", 0), "hot_share_of_node_visits": round(work.get("nodes_hot_closest", 0) / max(1, work["nodes_closest"]), 4),
+                        "launch_shape": "%d threads x %d block(s) per CU" % (tinfo.get("block_threads", 256), tinfo.get("blocks_per_cu", 6))}
+            if traffic:
+                roofline["achieved"] = round(traffic["bytes_per_launch"] / (avg_launch_ms * 1e-3) * 1e-9, 1)
+                roofline["frac"] = round(roofline["achieved"] / HBM_PEAK_GBS, 4)
+                roofline["alg_over_hbm_bytes"] = round(roofline["alg_bytes_per_launch"] / traffic["bytes_per_launch"], 2)
             try:
-                vi = valu_live(wl_args, 1)
-                if vi and clk_ghz:
-                    # CUs from the persistent launch itself: waves per launch = CUs x blocks per CU x waves per block
-                    simds = 4 * max(1, int(round(vi["waves_per_launch"] / (tinfo.get("blocks_per_cu", 6) * tinfo.get("block_threads", 256) / 64.0))))
-                    launch_cycles = avg_launch_ms * 1e-3 * clk_ghz * 1e9
-                    per_simd = vi["valu_insts_per_launch"] / simds
-                    vi["simd_cycles_per_valu_inst"] = round(launch_cycles / per_simd, 3)      # what one VALU instruction of this kernel costs its SIMD, all stalls included
-                    vi["probe_cycles_per_valu_inst"] = PROBE_MIX_CYCLES                        # the same SIMD saturated with the box test's mix (tools/valu_probe)
-                    vi["issue_frac"] = round(PROBE_MIX_CYCLES / vi["simd_cycles_per_valu_inst"], 4)
-                    vi["note"] = ("SQ counters of a separate rocprofv3 --pmc pass of this workload; launch time from the unprofiled run x the clock measured inside the kernel; "
-                                  "ceiling = tools/valu_probe2 kind 3 at 8 waves per SIMD (%.2f cycles per wave instruction; plain v_fma_f32 %.2f)" % (PROBE_MIX_CYCLES, PROBE_FMA_CYCLES))
-                    shade_sq = vi.pop("_shade", None)
-                    roofline["valu_issue"] = vi
-                    roofline["frac_valu_lane_throughput"] = round(vi["issue_frac"] * vi["lanes_active_per_valu_inst"] / 64.0, 4)
-                    # ... and the same figures for the shading kernel, from the same counter pass: k_shade has no memory roof worth the name (its
-                    # tables sit in the L2 / scalar cache); what bounds it is the rate at which its SIMDs issue VALU instructions, and how many lanes each one carries
-                    if shade_sq and timing.get("shade") and timing["shade"][1]:
-                        sh_ms = timing["shade"][0] / timing["shade"][1]          # live average launch time (HIP events on the ctx stream)
-                        sh_cycles = sh_ms * 1e-3 * clk_ghz * 1e9                  # (the clock measured inside the traversal launches of the same frame)
-                        per_simd_sh = shade_sq["valu_insts_per_launch"] / simds
-                        shade_sq["avg_launch_ms"] = round(sh_ms, 3)
-                        shade_sq["launches_per_step"] = timing["shade"][1] / args.steps
-                        shade_sq["simd_cycles_per_valu_inst"] = round(sh_cycles / per_simd_sh, 3)
-                        shade_sq["probe_cycles_per_valu_inst"] = PROBE_FMA_CYCLES   # a SIMD saturated with independent v_fma_f32 (tools/valu_probe2 kind 0): the arithmetic of shading is fma / mul / add
-                        shade_sq["issue_frac"] = round(PROBE_FMA_CYCLES / shade_sq["simd_cycles_per_valu_inst"], 4)
-                        shade_sq["frac_valu_lane_throughput"] = round(shade_sq["issue_frac"] * shade_sq["lanes_active_per_valu_inst"] / 64.0, 4)
-                        shade_sq["bound"] = "valu_issue"
-                        shade_sq["note"] = ("SQ counters of the same rocprofv3 --pmc pass as valu_issue; launch time live from this run; issue_frac = the measured issue rate of plain v_fma_f32 "
-                                            "(%.2f cycles per wave instruction per SIMD, profiles/r04_a_valu_probe2_issue_rate_and_clock.txt) / the SIMD cycles one VALU instruction of this kernel "
-                                            "costs, all stalls included; memory side (not measured in this run): 132.7 GB of read requests per 64 spp C3 frame = 1.03 TB/s, 0.13 of the 8 TB/s peak "
-                                            "(profiles/r06_w_kernel_traffic.txt, the same TCC_EA0_RDREQ pass as roofline.traffic, per kernel)" % PROBE_FMA_CYCLES)
-                        roofline_shade = shade_sq
+                roofline["hbm_stream_read_GBps"] = round(ctx.stream_read_gbps(4 << 30), 1)   # achievable ceiling, beside the spec peak
+                if roofline["achieved"]:
+                    roofline["frac_of_stream_ceiling"] = round(roofline["achieved"] / roofline["hbm_stream_read_GBps"], 4)
             except Exception as e:   # measurement aid only
-                log("[bench] VALU issue figure not measured: %s" % e)
-        # the three named fractions: SURVEY.md s.8(d)'s algorithmic bytes against the HBM peak (> 1: served by LDS / L2 / MALL, not an HBM
-        # quantity), the counter-measured HBM fraction (= `frac`; the north star's >= 0.40 target is NOT met and HBM is not the binding roof), and the roof
-        # that binds: VALU issue x lane occupancy
-        roofline["frac_alg_8d"] = round(roofline["alg_bytes_per_launch"] / (avg_launch_ms * 1e-3) * 1e-9 / HBM_PEAK_GBS, 4) if avg_launch_ms > 0 else None
-        roofline["frac_hbm_counter"] = roofline["frac"]
-        roofline["binding_roof"] = "VALU issue (frac_valu_lane_throughput = issue_frac x lanes_active / 64); HBM target of the north star (>= 0.40 of 8 TB/s in this kernel) unmet"
-        # the line itself says what is true: `bound` names the roof `frac` is quoted against (the contract's HBM figure, from calibrated counters),
-        # `bound_actual` the roof that binds, and the north star's >= 0.40 HBM target is reported as a boolean
-        roofline["bound_actual"] = "valu_issue"
-        roofline["hbm_target"] = {"north_star": ">= 0.40 of the 8 TB/s HBM peak in the traversal kernel", "met": bool(roofline.get("frac") is not None and roofline["frac"] >= 0.40),
-                                  "note": "frac counts the L2's memory-side requests by size; Infinity-Cache (MALL, 256 MiB) hits are included -- no counter of this tool separates them "
-                                          "(TCC_EA0_RDREQ_DRAM equals TCC_EA0_RDREQ) -- so true HBM utilisation is <= frac"}
+                log("[bench] stream-read ceiling not measured: %s" % e)
+            # What the traversal IS bound by: the rate at which a CU serves incoherent 16-byte loads.  achieved = the kernel's own
+            # lane requests (node words + triangle vertices + the ray record, from the counting pass) / its launch time; ceiling = mi_gather_rate:
+            # chains of dependent random fetches of records of the node size from a buffer of the node array's size, same launch shape, no arithmetic.
+            try:
+                loads = max(1, min(4, tinfo["node_bytes"] // 16))
+                # vector-memory lane requests: the node steps NOT served from LDS, the triangle vertices, the ray record
+                req_per_step = (work["nodes_closest"] - work.get("nodes_hot_closest", 0)) * (tinfo["node_bytes"] // 16) + work["tris_closest"] * 3 + ext_rays * 3
+                ach = req_per_step / (t_closest_ms * 1e-3) * 1e-9 if t_closest_ms > 0 else 0.0
+                node_mb = max(1, (tinfo["nodes"] * tinfo["node_bytes"]) >> 20)
+                ladder = {}   # the same chain of dependent record fetches over working sets that sit in the L1s, the L2s, the Infinity Cache, HBM
+                for name, nbytes in (("L1_32KB", 32 << 10), ("L2_2MB", 2 << 20), ("MALL_64MB", 64 << 20), ("HBM_%dMB_node_array" % node_mb, node_mb << 20)):
+                    ladder[name] = round(ctx.gather_rate(nbytes, loads), 1)
+                roofline["request_rate"] = {"achieved_Greq_per_s": round(ach, 1), "requests_per_ray": round(req_per_step / max(1, ext_rays), 1),
+                                            "ceilings_Greq_per_s": ladder, "frac_of_L2_resident_ceiling": round(ach / ladder["L2_2MB"], 4) if ladder["L2_2MB"] > 0 else None,
+                                            "ceilings_are": "mi_gather_rate: chains of dependent random %d x 16 B record fetches per lane over a buffer of the stated size, "
+                                                            "traversal launch shape, no arithmetic; the traversal's own fetches are a MIX of these levels (upper tree levels are shared)" % loads}
+            except Exception as e:   # measurement aid only
+                log("[bench] request-rate ceiling not measured: %s" % e)
+            # ... and what does bound it: VALU issue.  Everything here is measured: the launch's SIMD cycles = live launch time x the shader
+            # clock the kernel itself reports (s_memtime / s_memrealtime per wave, mi_trace_clock); its VALU instructions per SIMD from a separate rocprofv3 --pmc
+            # pass; the ceiling from tools/valu_probe (profiles/r04_a_valu_probe2_issue_rate_and_clock.txt: a SIMD issues the box test's instruction mix at
+            # 3.39 cycles per wave instruction with 8 waves resident, plain v_fma_f32 at 2.2; profiles/r04_c_issue_probe_instruction_costs.txt per instruction).
+            clk_ghz = (trace_clk or {}).get("closest_GHz") or 0.0
+            if clk_ghz:
+                roofline["shader_clock_GHz"] = {"closest": round(trace_clk["closest_GHz"], 3), "anyhit": round(trace_clk["anyhit_GHz"], 3),
+                                                "source": "s_memtime / s_memrealtime ticks per wave inside the launches of the counting pass (mi_trace_clock)"}
+            if world == 1 and args.traffic == "live":
+                try:
+                    vi = valu_live(wl_args, 1)
+                    if vi and clk_ghz:
+                        # CUs from the persistent launch itself: waves per launch = CUs x blocks per CU x waves per block
+                        simds = 4 * max(1, int(round(vi["waves_per_launch"] / (tinfo.get("blocks_per_cu", 6) * tinfo.get("block_threads", 256) / 64.0))))
+                        launch_cycles = avg_launch_ms * 1e-3 * clk_ghz * 1e9
+                        per_simd = vi["valu_insts_per_launch"] / simds
+                        vi["simd_cycles_per_valu_inst"] = round(launch_cycles / per_simd, 3)      # what one VALU instruction of this kernel costs its SIMD, all stalls included
+                        vi["probe_cycles_per_valu_inst"] = PROBE_MIX_CYCLES                        # the same SIMD saturated with the box test's mix (tools/valu_probe)
+                        vi["issue_frac"] = round(PROBE_MIX_CYCLES / vi["simd_cycles_per_valu_inst"], 4)
+                        vi["note"] = ("SQ counters of a separate rocprofv3 --pmc pass of this workload; launch time from the unprofiled run x the clock measured inside the kernel; "
+                                      "ceiling = tools/valu_probe2 kind 3 at 8 waves per SIMD (%.2f cycles per wave instruction; plain v_fma_f32 %.2f)" % (PROBE_MIX_CYCLES, PROBE_FMA_CYCLES))
+                        shade_sq = vi.pop("_shade", None)
+                        roofline["valu_issue"] = vi
+                        roofline["frac_valu_lane_throughput"] = round(vi["issue_frac"] * vi["lanes_active_per_valu_inst"] / 64.0, 4)
+                        # ... and the same figures for the shading kernel, from the same counter pass: k_shade has no memory roof worth the name (its
+                        # tables sit in the L2 / scalar cache); what bounds it is the rate at which its SIMDs issue VALU instructions, and how many lanes each one carries
+                        if shade_sq and timing.get("shade") and timing["shade"][1]:
+                            sh_ms = timing["shade"][0] / timing["shade"][1]          # live average launch time (HIP events on the ctx stream)
+                            sh_cycles = sh_ms * 1e-3 * clk_ghz * 1e9                  # (the clock measured inside the traversal launches of the same frame)
+                            per_simd_sh = shade_sq["valu_insts_per_launch"] / simds
+                            shade_sq["avg_launch_ms"] = round(sh_ms, 3)
+                            shade_sq["launches_per_step"] = timing["shade"][1] / args.steps
+                            shade_sq["simd_cycles_per_valu_inst"] = round(sh_cycles / per_simd_sh, 3)
+                            shade_sq["probe_cycles_per_valu_inst"] = PROBE_FMA_CYCLES   # a SIMD saturated with independent v_fma_f32 (tools/valu_probe2 kind 0): the arithmetic of shading is fma / mul / add
+                            shade_sq["issue_frac"] = round(PROBE_FMA_CYCLES / shade_sq["simd_cycles_per_valu_inst"], 4)
+                            shade_sq["frac_valu_lane_throughput"] = round(shade_sq["issue_frac"] * shade_sq["lanes_active_per_valu_inst"] / 64.0, 4)
+                            shade_sq["bound"] = "valu_issue"
+                            shade_sq["note"] = ("SQ counters of the same rocprofv3 --pmc pass as valu_issue; launch time live from this run; issue_frac = the measured issue rate of plain v_fma_f32 "
+                                                "(%.2f cycles per wave instruction per SIMD, profiles/r04_a_valu_probe2_issue_rate_and_clock.txt) / the SIMD cycles one VALU instruction of this kernel "
+                                                "costs, all stalls included; memory side (not measured in this run): 132.7 GB of read requests per 64 spp C3 frame = 1.03 TB/s, 0.13 of the 8 TB/s peak "
+                                                "(profiles/r06_w_kernel_traffic.txt, the same TCC_EA0_RDREQ pass as roofline.traffic, per kernel)" % PROBE_FMA_CYCLES)
+                            roofline_shade = shade_sq
+                except Exception as e:   # measurement aid only
+                    log("[bench] VALU issue figure not measured: %s" % e)
+            # the three named fractions: SURVEY.md s.8(d)'s algorithmic bytes against the HBM peak (> 1: served by LDS / L2 / MALL, not an HBM
+            # quantity), the counter-measured HBM fraction (= `frac`; the north star's >= 0.40 target is NOT met and HBM is not the binding roof), and the roof
+            # that binds: VALU issue x lane occupancy
+            roofline["frac_alg_8d"] = round(roofline["alg_bytes_per_launch"] / (avg_launch_ms * 1e-3) * 1e-9 / HBM_PEAK_GBS, 4) if avg_launch_ms > 0 else None
+            roofline["frac_hbm_counter"] = roofline["frac"]
+            roofline["binding_roof"] = "VALU issue (frac_valu_lane_throughput = issue_frac x lanes_active / 64); HBM target of the north star (>= 0.40 of 8 TB/s in this kernel) unmet"
+            # the line itself says what is true: `bound` names the roof `frac` is quoted against (the contract's HBM figure, from calibrated counters),
+            # `bound_actual` the roof that binds, and the north star's >= 0.40 HBM target is reported as a boolean
+            roofline["bound_actual"] = "valu_issue"
+            roofline["hbm_target"] = {"north_star": ">= 0.40 of the 8 TB/s HBM peak in the traversal kernel", "met": bool(roofline.get("frac") is not None and roofline["frac"] >= 0.40),
+                                      "note": "frac counts the L2's memory-side requests by size; Infinity-Cache (MALL, 256 MiB) hits are included -- no counter of this tool separates them "
+                                              "(TCC_EA0_RDREQ_DRAM equals TCC_EA0_RDREQ) -- so true HBM utilisation is <= frac"}
         kernel_ms = {k: round(v[0] / args.steps, 3) for k, v in timing.items() if v[1]}
 
         # ---- CPU baseline beside it (rank 0, N = 1): the REFERENCE's own multithreaded path -- oracle/_ref/pbrt_ref, built from the
@@ -697,7 +737,7 @@ def main():
         # (stamped by the build shim, PBRT_REF_RENDER_TIMES), samples / rays from its own statistics.  The oracle port is
         # timed as a second sample.  Reported baselines, not targets.
         cpu = None
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             import oracle_lib as ol
             ncores = host_cpus()
             cpu = cpu_reference(sc, scene_file, ncores, args.cpu_seconds, ol)
@@ -712,12 +752,13 @@ def main():
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "config": {"workload": workload, "tiles": "16x16, 2-D lattice over ranks (mi_tile_owner)", "parallelism": "tile-sharded x%d" % world},
-               "mrays_per_s": round(mrays, 2), "rays_per_sample": round(samples[1] / max(1.0, samples[0]), 3),
-               "roofline": roofline, "roofline_shade": roofline_shade, "cpu_baseline": cpu, "kernel_ms_per_step": kernel_ms,
+               "mrays_per_s": round(mrays, 2), "rays_per_sample": round(samples[1] / max(1.0, samples[0]), 3), "kernel_ms_per_step": kernel_ms,
                "setup_s": {"parse_and_bvh_build": round(t_load, 2), "upload_and_bvh4": round(t_upload, 2),
                            "scene": "rank 0 of the node builds it once, the other ranks map the published blob" if world > 1 else "built"}}
         if world > 1:
             out["setup_s"]["scene_by_rank"] = scene_sources
+        if args.full:
+            out.update({"roofline": roofline, "roofline_shade": roofline_shade, "cpu_baseline": cpu})
     phase("closing")
     frame.close()
     ctx.close()
@@ -726,7 +767,7 @@ def main():
         # ---- the San-Miguel-like variant beside the headline: what the real scene is -- textured, bump-mapped materials and alpha-masked foliage --
         # rendered by a child process once this process has released the GPU memory of the headline frame; the headline workload itself is unchanged
         plain_c3 = args.config == "c3" and not (args.textured or args.leafmask or args.volpath or args.fogbox or args.subsurface or args.smokebox or args.scene)
-        if world == 1 and (args.secondary == "on" or (args.secondary == "auto" and plain_c3 and args.spp == 64 and args.tris == 10_000_000 and args.cpu_seconds > 0)):
+        if args.full and world == 1 and (args.secondary == "on" or (args.secondary == "auto" and plain_c3 and args.spp == 64 and args.tris == 10_000_000 and args.cpu_seconds > 0)):
             out["secondary"] = {"textured_leafmask": secondary_line(["--textured", "--leafmask", "--tris", str(args.tris), "--res", str(args.res[0]), str(args.res[1]), "--spp", str(args.spp)])}
         print(json.dumps(out), flush=True)
         # parity at full size is part of the measurement: a frame that does not match the reference's is not a result

@@ -26,14 +26,31 @@ ORACLE = os.path.join(ROOT, "oracle", "liboracle.so")
 
 CASES = [("cornell", os.path.join(ROOT, "scenes", "cornell.pbrt"), []),
          ("materials", os.path.join(ROOT, "scenes", "materials.pbrt"), []),
-         # the reference's own example scene, unmodified: Sphere area light, Halton sampler, Loop subdivision surfaces
-         ("killeroo-simple", "/root/reference/scenes/killeroo-simple.pbrt", ["--cropwindow", "0.3", "0.7", "0.3", "0.7"])]
+         # the reference's example scene killeroo-simple: Sphere area light, Halton sampler, Loop subdivision surfaces (_killeroo_scene)
+         ("killeroo-simple", None, ["--cropwindow", "0.3", "0.7", "0.3", "0.7"])]
+
+# a Loop subdivision surface of the test's own (an octahedron, 3 levels) in front of the two killeroos, inside the crop window
+LOOP_SURFACE = ('AttributeBegin\n  Material "plastic" "color Kd" [.2 .3 .5] "color Ks" [.4 .4 .4] "float roughness" [.05]\n  Translate 160 46 -54\n  Scale 18 18 18\n'
+                '  Shape "loopsubdiv" "integer levels" [3] "point P" [1 0 0  -1 0 0  0 1 0  0 -1 0  0 0 1  0 0 -1]\n'
+                '    "integer indices" [0 2 4  2 1 4  1 3 4  3 0 4  2 0 5  1 2 5  3 1 5  0 3 5]\nAttributeEnd\n')
+
+
+def _killeroo_scene(tmp_path):
+    """scenes/killeroo.pbrt -- killeroo-simple with its two Loop-subdivided killeroos as PLY (tools/make_killeroo.py) -- plus LOOP_SURFACE, so the reference's
+    LoopSubdiv still produces a shape the stub hands over"""
+    text = open(os.path.join(ROOT, "scenes", "killeroo.pbrt")).read()
+    text = text.replace("killeroo_geo/", os.path.join(ROOT, "scenes", "killeroo_geo") + "/").replace("WorldEnd", LOOP_SURFACE + "WorldEnd")
+    scene = tmp_path / "killeroo-simple.pbrt"
+    scene.write_text(text)
+    return str(scene)
 
 
 @pytest.mark.parametrize("name,scene,extra", CASES, ids=[c[0] for c in CASES])
 def test_reference_scene_through_the_stub_equals_pbrt_ref(name, scene, extra, tmp_path):
     if not (os.access(REF, os.X_OK) and os.access(STUB, os.X_OK)):
         pytest.skip("oracle/_ref/pbrt_ref[_flatcheck] not built here (needs /root/reference)")
+    if scene is None:
+        scene = _killeroo_scene(tmp_path)
     if not os.path.exists(scene):
         pytest.skip("scene file not present: %s" % scene)
     a, b = str(tmp_path / "stub.pfm"), str(tmp_path / "ref.pfm")

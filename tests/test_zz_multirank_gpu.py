@@ -120,6 +120,41 @@ def test_bench_one_rank_film_equals_the_library_render(tmp_path):
     ctx.close()
 
 
+def test_bench_plain_line_times_the_steps_and_dumps_the_film(tmp_path):
+    """a plain run (no --full): exactly --steps timed steps, the headline fields and no more, and --dump-outputs writes the last timed step's film -- the film
+    the library renders in-process for the same scene file"""
+    out_dir = tmp_path / "outputs"
+    rc, out, err = run_job(["--gpus", "1", "--dump-outputs", str(out_dir)] + SMALL + ["--steps", "3"], tmp_path)
+    assert rc == 0, err[-3000:]
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out[-500:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] * 1e6 * d["ms_per_step"] * 1e-3 - 320 * 192 * 4) <= 0.01 * 320 * 192 * 4   # one step = every sample of the frame once
+    assert not {"roofline", "roofline_shade", "cpu_baseline", "secondary"} & set(d), sorted(d)
+    assert sorted(os.listdir(out_dir)) == ["film.npy"]
+    got = np.load(out_dir / "film.npy")
+    assert got.dtype == np.float32
+    sc = pa.Scene(os.path.join(str(tmp_path), SCENE_KEY, "sanmiguel_synth.pbrt"), strict=True)
+    ctx = pa.Context(sc)
+    ctx.render()
+    ref = ctx.film()
+    ctx.close()
+    assert got.shape == ref.shape == (192, 320, 4)
+    own_only = ref[..., 3] == sc.info["spp"]
+    assert np.array_equal(got[own_only].view(np.uint32), ref[own_only].view(np.uint32))
+
+
+def test_bench_full_keeps_the_roofline(tmp_path):
+    """--full still measures what moved out of the plain run: the counting pass behind the roofline's per-ray figures and the stream / gather ceilings"""
+    rc, out, err = run_job(["--gpus", "1", "--full", "--secondary", "off"] + SMALL, tmp_path)
+    assert rc == 0, err[-3000:]
+    d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    r = d["roofline"]
+    assert r["nodes_per_ray"] > 1 and r["tris_per_ray"] > 0 and r["hbm_stream_read_GBps"] > 0 and r["request_rate"]["ceilings_Greq_per_s"]["L2_2MB"] > 0
+    assert "cpu_baseline" in d and d["cpu_baseline"] is None   # --cpu-seconds 0
+
+
 def test_a_cut_off_scene_file_fails_both_ranks_loudly(tmp_path):
     """A PLY file shorter than its header promises (cut off, or caught half-written) is an ERROR on the rank that reads it -- never a smaller scene: local rank 0
     fails its strict load and announces why, rank 1 stops waiting and fails with that reason (or is ended by the launcher first), the job ends non-zero well

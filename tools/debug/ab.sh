@@ -1,7 +1,7 @@
 #!/bin/bash
 cd /root/repo; mkdir -p gpurun_out
 timeout 600 python -m pytest tests -m gpu -x -q 2>&1 | tail -4
-run() { timeout 300 python bench.py --spp 16 --steps 2 --warmup 1 --cpu-seconds 0 2>gpurun_out/s4_$1.err | python -c "
+run() { timeout 300 python bench.py --full --spp 16 --steps 2 --warmup 1 --cpu-seconds 0 | python -c "
 import json,sys
 d=json.load(sys.stdin); r=d['roofline']
 print('$1', d['value'], d['kernel_ms_per_step'], 'nodes/ray', round(r['nodes_per_ray'],2), 'tris/ray', round(r['tris_per_ray'],2))"; }
